@@ -8,11 +8,21 @@
 
 One "step" = forward + cross-entropy + backward + (N>1: flat-buffer RCCL all-reduce) + global-norm clip + fused AdamW +
 LR update over one synthetic batch already resident in HBM (token ids with their host-side non-pad counts, as the data
-loader hands them over: the text encoder runs pad-free).  Rank 0 prints ONE JSON line (contract in the task prompt) with
-extra objects: ``roofline`` for the dominant kernel family (timed live with HIP events on the launch stream, in one
-instrumented single-stream step outside the timed region), ``cpu_baseline`` (the oracle port timed on the host cores,
-BASELINE.md section 4 protocol; N=1 only) and ``inference`` (BASELINE configs[3]: the eval forward at batch 256 captured in a
-hipGraph and replayed; N=1 only).  ``--mode infer --batch 256`` prints that leg as the headline line instead.
+loader hands them over: the text encoder runs pad-free).  Rank 0 prints ONE JSON line: ``metric``, ``value``, ``unit``,
+``higher_is_better``, ``dtype``, ``ms_per_step`` (wall time of one timed step) and the run's configuration.
+
+A plain run does only what that line needs: set-up, ``--warmup`` steps, ``--steps`` timed steps, the line.  ``--full`` adds
+the measurements beside the headline, each in runs of its own after the timed steps: ``roofline`` for the dominant kernel
+family (timed live with HIP events on the launch stream, in one instrumented single-stream step), the host enqueue cost,
+algorithmic FLOP figures, ``varlen_text`` and ``host_fed_inputs``, ``cpu_baseline`` (the oracle port timed on the host cores,
+BASELINE.md section 4 protocol; N=1 only), ``inference`` (BASELINE configs[3]: the eval forward at batch 256 captured in a
+hipGraph and replayed; N=1 only) and ``fp8`` (BASELINE configs[4]).  ``--mode infer --batch 256`` prints the inference leg as
+the headline line instead.
+
+``--dump-outputs DIR`` writes what the timed path computed in its last timed step as float32 ``DIR/<name>.npy``: train mode
+``loss``, ``logits`` (eager step only), ``grad_norm`` and ``params_sample`` (a fixed, seeded sample of the updated fp32 master
+weights); infer mode ``logits``.  Inputs, weights and dropout masks are seeded, so runs with the same arguments see the same
+inputs; the outputs of two runs agree up to the summation order of the fp32 atomic reductions, not bit for bit.
 """
 import argparse
 import contextlib
@@ -59,7 +69,31 @@ def parse():
     ap.add_argument("--cpu-budget-s", type=float, default=240.0, help="safety bound on the CPU baseline leg: the timed runs stop once this much time is spent (the full protocol, 2 warm-ups + 5 runs of ~22 s, takes ~150 s)")
     ap.add_argument("--cpu-threads", type=int, default=64, help="cap on the CPU baseline's torch threads (0 = every physical core)")
     ap.add_argument("--no-fp8", action="store_true", help="train mode: skip the extra fp8 legs (BASELINE configs[4]: train step + batch-256 inference)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every measurement beside the headline (roofline, "
+                    "host enqueue cost, FLOP figures, varlen_text, host_fed_inputs, inference, fp8, cpu_baseline; the --no-* options "
+                    "above skip single ones); off: the plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step to DIR/<name>.npy (float32)")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 22          # fp32 master weights written by --dump-outputs: a fixed, seeded sample of this many (16 MB)
+
+
+def dump_outputs(path, arrays):
+    """arrays: {name: tensor} -> path/<name>.npy in float32."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
+def params_sample(store):
+    """A fixed, seeded sample of the flat fp32 master weights (all of them when there are fewer than DUMP_SAMPLE)."""
+    if store.total <= DUMP_SAMPLE:
+        return store.flat
+    idx = torch.randint(store.total, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    return store.flat[idx.to(store.flat.device)]
 
 
 def build(args, device, rank):
@@ -127,9 +161,13 @@ def main():
 
     config, model, opt, sched, batch = build(args, device, rank)
     if args.mode == "infer":
-        out = infer_leg(args, config, model, device, world_size(), steps=args.steps, warmup=args.warmup)
-        out["cpu_baseline"] = None
+        outputs = {}
+        out = infer_leg(args, config, model, device, world_size(), steps=args.steps, warmup=args.warmup, full=args.full, outputs=outputs)
+        if args.full:
+            out["cpu_baseline"] = None
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, outputs)
             print(json.dumps(out))
         if world_size() > 1:
             dist.barrier()
@@ -152,7 +190,7 @@ def main():
         opt.zero_grad()
         sched.step_update(it[0])
         it[0] += 1
-        return loss
+        return loss, logits
 
     def fence():
         torch.cuda.synchronize()
@@ -180,14 +218,14 @@ def main():
             opt.dev_hyper = None
             model.max_steps_in_flight = 2
             torch.cuda.synchronize()
-    run = (lambda: graphed.step()[0]) if graphed is not None else step
+    run = (lambda: (graphed.step()[0], None)) if graphed is not None else step      # the captured step keeps no logits
 
     for _ in range(args.warmup):
         run()
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = run()
+        loss, logits = run()
     host_ms = (time.perf_counter() - t0) / args.steps * 1e3        # host time per step (the GPU runs behind it)
     fence()
     dt = time.perf_counter() - t0
@@ -199,10 +237,25 @@ def main():
     n_fn = args.batch * world_size() * args.steps
     value = n_fn / dt
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:            # before anything below runs another step
+        outputs = {"loss": loss.reshape(1), "grad_norm": store.norm[:1], "params_sample": params_sample(store)}
+        if logits is not None:
+            outputs["logits"] = logits
+        dump_outputs(args.dump_outputs, outputs)
 
     if graphed is not None:
         it[0] = graphed.it
         graphed.close()
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world_size(), value, ms_per_step, graph_note, lens, ids, loss_val)))
+        if world_size() > 1:
+            dist.barrier()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
+
+    # --full from here on: every measurement beside the headline, each in runs of its own
     # host cost of enqueueing one step from Python, with the two-steps-in-flight throttle off (3 steps queue up behind the GPU)
     fence()
     model.max_steps_in_flight = 0
@@ -343,22 +396,14 @@ def main():
 
     if rank == 0:
         fl = algorithmic_flops_per_function(config)
-        out = {
-            "metric": "functions/sec (train step)", "value": round(value, 3), "unit": "functions/s", "n_gpus": world_size(),
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": "fused MVulD train step: SwinV2-base 448x448 (window 28) + UniXcoder 12x768 @512 tokens + "
-                                   "GAT/Rs_GCN head on ~200-node graphs; fwd+CE+bwd+clip+AdamW, random-init weights",
-                       "batch_per_gpu": args.batch, "global_batch": args.batch * world_size(), "parallelism": f"dp{world_size()}",
-                       "algorithmic_tflop_per_step_per_gpu": round(fl * args.batch / 1e12, 2),
-                       "achieved_tflops_per_gpu": round(fl * args.batch / (ms_per_step * 1e-3) / 1e12, 2),
-                       "frac_of_dense_bf16_peak": round(fl * args.batch / (ms_per_step * 1e-3) / PEAK_BF16, 4),
-                       "step_launch": graph_note,
-                       "host_enqueue_ms_per_step": round(host_ms_reported, 3),
-                       "host_enqueue_eager_ms_per_step": round(host_unthrottled_ms, 2),
-                       "text_tokens_nonpad_frac": round(float(lens.sum()) / ids.numel(), 4), "final_loss": round(loss_val, 5)},
-            "roofline": roofline, "cpu_baseline": cpu, "inference": inference, "fp8": fp8, "varlen_text": varlen, "host_fed_inputs": host_fed,
-        }
+        out = headline(args, world_size(), value, ms_per_step, graph_note, lens, ids, loss_val)
+        out["config"].update({"algorithmic_tflop_per_step_per_gpu": round(fl * args.batch / 1e12, 2),
+                              "achieved_tflops_per_gpu": round(fl * args.batch / (ms_per_step * 1e-3) / 1e12, 2),
+                              "frac_of_dense_bf16_peak": round(fl * args.batch / (ms_per_step * 1e-3) / PEAK_BF16, 4),
+                              "host_enqueue_ms_per_step": round(host_ms_reported, 3),
+                              "host_enqueue_eager_ms_per_step": round(host_unthrottled_ms, 2)})
+        out.update({"roofline": roofline, "cpu_baseline": cpu, "inference": inference, "fp8": fp8, "varlen_text": varlen,
+                    "host_fed_inputs": host_fed})
         print(json.dumps(out))
     if world_size() > 1:
         dist.barrier()
@@ -366,10 +411,26 @@ def main():
         dist.destroy_process_group()
 
 
-def infer_leg(args, config, model, device, world, steps=5, warmup=2):
+def headline(args, world, value, ms_per_step, graph_note, lens, ids, loss_val):
+    """The result line of the train step: what a plain run prints; --full adds its measurements to it."""
+    return {
+        "metric": "functions/sec (train step)", "value": round(value, 3), "unit": "functions/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": "fused MVulD train step: SwinV2-base 448x448 (window 28) + UniXcoder 12x768 @512 tokens + "
+                               "GAT/Rs_GCN head on ~200-node graphs; fwd+CE+bwd+clip+AdamW, random-init weights",
+                   "batch_per_gpu": args.batch, "global_batch": args.batch * world, "parallelism": f"dp{world}",
+                   "step_launch": graph_note,
+                   "text_tokens_nonpad_frac": round(float(lens.sum()) / ids.numel(), 4), "final_loss": round(loss_val, 5)},
+    }
+
+
+def infer_leg(args, config, model, device, world, steps=5, warmup=2, full=True, outputs=None):
     """BASELINE configs[3]: inference-only fused forward at `infer_batch` functions per GPU, captured ONCE in a hipGraph (both
     streams, every launch through the C ABI, pad-free text encoder from a precomputed packing plan) and replayed.
-    Returns the dict bench.py prints (mode infer) or embeds under "inference" (mode train)."""
+    Returns the dict bench.py prints (mode infer) or embeds under "inference" (mode train).  full=False leaves out what the
+    timing does not need (the replay-equals-eager check, the roofline, the FLOP figures); `outputs`, a dict, receives the
+    logits of the last timed replay."""
     from mvuld_amd import hip
     from mvuld_amd.data import synthetic
     from mvuld_amd.models.unixcoder import RobertaModel
@@ -410,9 +471,11 @@ def infer_leg(args, config, model, device, world, steps=5, warmup=2):
             tt = torch.tensor([dt], device=device)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt)
-        same = bool(torch.equal(out.float(), eager))
+        if outputs is not None:
+            outputs["logits"] = out.float().clone()
+        same = bool(torch.equal(out.float(), eager)) if full else None
         roofline = None
-        if not args.no_kernel_timing:
+        if full and not args.no_kernel_timing:
             hip.TIMING.enable()
             model(g, images, ids, seq_lens=plan)
             torch.cuda.synchronize()
@@ -421,17 +484,19 @@ def infer_leg(args, config, model, device, world, steps=5, warmup=2):
             roofline = make_roofline(fam, dt / steps * 1e3)
         del graph, out
     model.train(was_training)
-    fl = algorithmic_flops_per_function(config) / 3.0                           # forward only
     ms = dt / steps * 1e3
-    return {"metric": "functions/sec (inference, hipGraph-captured fused forward)", "value": round(B * world * steps / dt, 3), "unit": "functions/s",
-            "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": "fused MVulD eval forward (BASELINE configs[3]): SwinV2-base 448x448 + UniXcoder 12x768 @512 tokens (pad-free) + "
-                                   "GAT/Rs_GCN head, one hipGraph replay per step", "batch_per_gpu": B, "global_batch": B * world,
-                       "parallelism": f"replicas x{world}", "graph_replay_equals_eager": same,
-                       "algorithmic_tflop_per_step_per_gpu": round(fl * B / 1e12, 2),
-                       "frac_of_dense_bf16_peak": round(fl * B / (ms * 1e-3) / PEAK_BF16, 4)},
-            "roofline": roofline}
+    res = {"metric": "functions/sec (inference, hipGraph-captured fused forward)", "value": round(B * world * steps / dt, 3), "unit": "functions/s",
+           "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+           "config": {"workload": "fused MVulD eval forward (BASELINE configs[3]): SwinV2-base 448x448 + UniXcoder 12x768 @512 tokens (pad-free) + "
+                                  "GAT/Rs_GCN head, one hipGraph replay per step", "batch_per_gpu": B, "global_batch": B * world,
+                      "parallelism": f"replicas x{world}"}}
+    if full:
+        fl = algorithmic_flops_per_function(config) / 3.0                       # forward only
+        res["config"].update({"graph_replay_equals_eager": same, "algorithmic_tflop_per_step_per_gpu": round(fl * B / 1e12, 2),
+                              "frac_of_dense_bf16_peak": round(fl * B / (ms * 1e-3) / PEAK_BF16, 4)})
+        res["roofline"] = roofline
+    return res
 
 
 # Kernel families of the instrumented step -> the groups `roofline` ranks.  Every attention launch (forward, the backward passes, the

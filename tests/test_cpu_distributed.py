@@ -15,7 +15,14 @@ def _free_port():
     return p
 
 
+def _cpu_only():
+    """The workers test the gloo (CPU) path.  On a machine with a GPU, init_distributed would bind rank r to device r, which a
+    one-GPU machine does not have: each worker process sees no GPU, as on a CPU-only machine."""
+    torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, out):
+    _cpu_only()
     os.environ.update({"RANK": str(rank), "WORLD_SIZE": str(world), "LOCAL_RANK": str(rank), "MASTER_ADDR": "127.0.0.1",
                        "MASTER_PORT": str(port)})
     import sys
@@ -68,6 +75,7 @@ def _worker_wiring(rank, world, port, out):
     """bench.py / main_bigvul.py's data-parallel wiring end to end on a real (CPU) ParamStore under gloo: parameter broadcast,
     attach_gradient_exchange's hooks fired in the order backward fires them, finish(), 1/world factor -- everything but the kernels
     and the backend string."""
+    _cpu_only()
     os.environ.update({"RANK": str(rank), "WORLD_SIZE": str(world), "LOCAL_RANK": str(rank), "MASTER_ADDR": "127.0.0.1",
                        "MASTER_PORT": str(port)})
     import sys
@@ -119,6 +127,7 @@ def _worker_wiring(rank, world, port, out):
 
 def _worker_bf16(rank, world, port, out):
     """the bf16-payload exchange (north_star's 464 MB) equals the fp32 exchange to bf16 rounding."""
+    _cpu_only()
     os.environ.update({"RANK": str(rank), "WORLD_SIZE": str(world), "LOCAL_RANK": str(rank), "MASTER_ADDR": "127.0.0.1",
                        "MASTER_PORT": str(port)})
     import sys
